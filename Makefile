@@ -23,7 +23,7 @@ test-gpu: build
 	$(PYTHON) -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread
 
 bench: build
-	$(PYTHON) bench.py --steps 50
+	$(PYTHON) bench.py --steps 50 --full
 
 # kustomize config/, examples/, OLM bundle/ generated from the code
 manifests:

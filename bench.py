@@ -21,10 +21,16 @@ cross xGMI) and `--mode sharded` (descriptor / verdict / packet all-to-alls) are
 Data: synthetic (random-init 1M-flow table, random 5-tuples); inputs rotate over 4 pre-generated
 batches so no step re-reads a cached one.  Latency: per-packet time from the batch release stamp
 (s_memrealtime at the start of the step) to the packet's egress, sampled 1/16, p50 over the timed
-steps' last batch — the latency AT the headline throughput.  The low-latency path is measured
-separately (1 GPU, after the timed region): the persistent ring kernel (csrc/nfdp/ring.hip) with
-64-packet chunks published one at a time, host-clock publish -> completion-flag round trip
-(`p50_latency_us_ring`), plus the throughput-mode ring's Mpps with 32 x 4096 packets in flight.
+steps' last batch — the latency AT the headline throughput.
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line: the headline
+alone.  `--dump-outputs DIR` also writes what the last timed step computed (dump_outputs).
+`--full` adds everything else the line can carry, each measured after the timed region in a run
+of its own: the exchange alone and unsteered traffic (N > 1), the small-batch latency probes, the
+low-latency path (1 GPU: the persistent ring kernel, csrc/nfdp/ring.hip, with 64-packet chunks
+published one at a time, host-clock publish -> completion-flag round trip, `p50_latency_us_ring`,
+plus the throughput-mode ring's Mpps with 64 x 4096 packets in flight), the traffic / rule-set
+variants, the SFC hop pipeline and the live pod-to-pod block.  Without it those keys are null.
 """
 from __future__ import annotations
 
@@ -239,6 +245,12 @@ def parse():
     ap.add_argument("--hash", default="lds", choices=["lds", "mfma"])
     ap.add_argument("--acl-mode", default="mfma", choices=["mfma", "scalar"])
     ap.add_argument("--rotate", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the result line can carry (exchange, "
+                         "unsteered, latency probes, ring, variants, hop pipeline, live block); the --no-* options "
+                         "trim it.  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-lowlat", action="store_true", help="skip the small-batch latency probe")
     ap.add_argument("--no-variants", action="store_true", help="skip the mixed / ACL1024 / IMIX measurements")
     ap.add_argument("--no-hops", action="store_true", help="skip the SFC hop pipeline across GPUs (tools/hop_bench.py)")
@@ -265,7 +277,44 @@ def parse():
     ap.add_argument("--rehearse", action="store_true",
                     help="correctness rehearsal of the N-GPU path on a 1-GPU box: every rank on cuda:0, gloo "
                          "with host-staged exchanges (RCCL refuses two ranks on one device); not a measurement")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:   # a plain run: the headline alone
+        a.no_lowlat = a.no_variants = a.no_hops = a.no_live = a.no_unsteered = True
+    return a
+
+
+DUMP_ROWS = 1 << 17   # rows --dump-outputs keeps of a larger array (egress slots: 32 MB as float32)
+
+
+def dump_outputs(d: str, arrays: dict, suffix: str = "") -> None:
+    """--dump-outputs: the arrays a caller of the timed path holds after the last timed step, as
+    `d/<name><suffix>.npy`.  N = 1 (fused kernel, device or host I/O): `out` and `meta`, row i of
+    each belonging to packet i of the last timed step's batch.  N > 1 claims less: one file set
+    per rank, holding what the rank's engine exposes once the timed steps are flushed.  rss /
+    replicated: `out` and `meta` as the rank's own kernel left them for its last batch - a packet
+    handed to another GPU shows only that hand-off (disposition 10); what its owner made of it
+    lies in the owner's receive buffers and is not written.  sharded: `meta` alone, the metadata
+    of the engine's pipeline slots concatenated (the chunks it ran last, not one batch in order).
+    8-bit data is
+    written as float32 and 32-bit words as float64, both exact.  Of an array with more than
+    DUMP_ROWS rows a fixed sample is kept: the same seeded, ascending row numbers for every array
+    of that length and every run, so two builds are compared row for row.  The latency samples
+    are not written: they are clock readings, not a function of the inputs."""
+    os.makedirs(d, exist_ok=True)
+    for name, x in arrays.items():
+        n = int(x.shape[0])
+        if n > DUMP_ROWS:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_ROWS, replace=False))
+            if isinstance(x, np.ndarray):
+                x = x[idx]
+            else:   # a tensor on the GPU: gather there, copy only the sample
+                import torch
+
+                x = x[torch.from_numpy(idx).to(x.device)]
+        x = np.asarray(x if isinstance(x, np.ndarray) else x.cpu().numpy())
+        if x.dtype.itemsize == 4:
+            x = x.view(np.uint32)
+        np.save(os.path.join(d, f"{name}{suffix}.npy"), x.astype(np.float32 if x.dtype.itemsize == 1 else np.float64))
 
 
 def _time_fused(dp, batches, steps, torch):
@@ -539,6 +588,10 @@ def main() -> None:
         def results():
             _, m = hp.results(0)
             return np.array(m), np.array(batch_ms[-64:]) * 1e3
+
+        def outputs():
+            o, m = hp.results((a.warmup + a.steps - 1) % hp.depth)   # the last timed step's slot
+            return {"out": np.array(o), "meta": np.array(m)}
     elif not sharded:
         out, meta, lat = dp.alloc_batch(a.batch)
 
@@ -548,6 +601,9 @@ def main() -> None:
 
         def results():
             return meta.cpu().numpy().view(np.uint32), lat.cpu().numpy().view(np.uint32).astype(np.float64) * 0.01
+
+        def outputs():
+            return {"out": out, "meta": meta}
     elif rss:
         eng = RssShardedDataPlane(dp, rank, world, a.batch, remote_frac=a.remote_frac)
 
@@ -579,6 +635,13 @@ def main() -> None:
         def results():
             return eng.out_meta(), eng.latency_samples_us()
 
+    if sharded:   # the multi-GPU engines: what this rank's engine holds after the flush (dump_outputs: N > 1)
+        def outputs():
+            arrs = {"meta": eng.out_meta()}
+            if hasattr(eng, "outputs"):
+                arrs["out"] = eng.outputs()
+            return arrs
+
     setup_s = time.time() - t_setup
     _log(f"setup done ({setup_s:.1f} s), warmup + timed steps")
     for k in range(a.warmup):
@@ -606,6 +669,9 @@ def main() -> None:
         elapsed = float(t.item())
 
     _log(f"timed region: {elapsed * 1e3 / a.steps:.4f} ms / step")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, outputs(), f".rank{rank}" if world > 1 else "")
+        _log(f"outputs of the last timed step written to {a.dump_outputs}")
     meta_np, lat_us = results()
     _, _, reasons = P.meta_fields(meta_np)
     fwd_local = float(np.mean((reasons == 0) | (reasons == 10)))  # 10: handed to its owner / egress GPU
@@ -621,7 +687,7 @@ def main() -> None:
     # exchange alone (outside the timed region, N > 1 replicated): the step's all-to-alls with no
     # compute around them -> achieved xGMI bandwidth per GPU and the exchange floor of a step
     xchg = None
-    if rss:
+    if rss and a.full:
         # the timed steps' traffic: packets this GPU handed to their owners (68 B each on xGMI)
         sent_per_step = eng.stats["sent"] / max(eng.stats["steps"], 1)
         max_peer = eng.stats["max_peer"]
@@ -646,7 +712,7 @@ def main() -> None:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
         xchg = rss_exchange_info(el / reps, sent_per_step, max_peer, a.remote_frac, eng.lag)
-    if replicated:
+    if replicated and a.full:
         s0 = eng.slots[0]
         for _ in range(3):
             eng.exchange(s0).wait()
@@ -717,9 +783,9 @@ def main() -> None:
 
     # host round trip of a small batch (outside the timed region, 1 GPU): submit -> results ready
     # on the host clock, with per-batch launches vs one replay of the captured HIP graph
-    _log("small-batch probes")
     rtt = None
     if not a.no_lowlat and world == 1 and a.io == "device" and not sharded:
+        _log("small-batch probes")
         nb = 256
         pk, im = batches[0][0][:nb].contiguous(), batches[0][1][:nb].contiguous()
         o3, m3, l3 = dp.alloc_batch(nb)
@@ -743,9 +809,9 @@ def main() -> None:
 
     # low-latency path (outside the timed region): persistent ring kernel, host publishes 64-packet
     # chunks and times publish -> completion flag on its own clock (dataplane/ring.py)
-    _log("ring kernel probes")
     ring = None
     if not a.no_lowlat and world == 1 and a.io == "device":
+        _log("ring kernel probes")
         from dpu_operator_amd.dataplane.ring import RingPath
 
         try:
@@ -756,7 +822,7 @@ def main() -> None:
             lat1, _ = rp.probe(batches=4000, batch=64, inflight=1)
             rp.stop()
             rp.close()
-            # loaded: throughput ring (every wave takes its own chunks), 32 x 4096 packets in flight.
+            # loaded: throughput ring (every wave takes its own chunks), 64 x 4096 packets in flight.
             # One trial is a few ms of GPU work, so a single host-thread stall (the host both
             # publishes and reaps) can halve it: 5 trials of 10000 batches, the median reported.
             # 64 chunks of 4096 in flight (tools/ring_ab.py, r6: 4,622 Mpps median against 2,869 at 32
@@ -786,17 +852,17 @@ def main() -> None:
     # realistic variants (1 GPU, after the timed region, same kernel and table): the headline is the
     # best case (every packet forwarded), so also report a mix with flow misses / ACL denies /
     # malformed frames, a 1024-rule ACL, and IMIX frame sizes (header path; payload stays in place)
-    _log("variants")
     variants = None
     if world == 1 and a.io == "device" and not a.no_variants:
+        _log("variants")
         variants = measure_variants(a, dp, sc, dev, torch, S, P)
 
     # SFC hop pipeline across GPUs (after the timed region): the headline chain split over two
     # data planes with the in-HBM hand-off between them - both on cuda:0 at N = 1, cuda:0 -> cuda:1
     # over xGMI at N > 1 (rank 0 measures while the other ranks wait at the barrier)
-    _log("hop pipeline")
     hops = None
     if a.io == "device" and not a.no_variants and not a.no_hops:
+        _log("hop pipeline")
         if world > 1:
             dist.barrier()
         if rank == 0:
@@ -808,9 +874,9 @@ def main() -> None:
     # live pod -> pod path (1 GPU, after the timed region): shared-memory pod vports, the native C++
     # I/O engine (csrc/nfdp/iox) and the persistent ring kernel; C++ pod generator / sinks measure
     # delivered Mpps and one-way latency on one clock (tools/live_bench.py)
-    _log("live block")
     live = live_veth = None
     if world == 1 and a.io == "device" and not a.no_live:
+        _log("live block")
         try:
             import importlib.util
 

@@ -24,8 +24,8 @@ from dpu_operator_amd import cpagent
 from dpu_operator_amd.cpagent import GET, H2F, SET, Reply
 
 A = cpagent.native()
-REF_CFG = Path("/root/reference/internal/daemon/vendor-specific-plugins/marvell/vendor/pcie_ep_octeon_target/"
-               "target/apps/octep_cp_agent/cn106xx.cfg")
+# the reference's octep_cp_agent/cn106xx.cfg, stored as a fixture
+REF_CFG = Path(__file__).resolve().parent / "golden" / "cn106xx.cfg"
 
 
 @pytest.fixture
@@ -101,8 +101,6 @@ def test_ring_rejects_peer_corrupted_cursors_and_geometry(tmp):
 
 
 def test_parse_reference_soc_config():
-    if not REF_CFG.exists():
-        pytest.skip("reference config not mounted")
     summary = A.config_summary(REF_CFG.read_text())
     pem_idx, pfs = summary[0]
     assert pem_idx == 0 and len(pfs) == 1

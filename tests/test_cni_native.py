@@ -4,7 +4,9 @@ result / error objects, DEL result ignored, CHECK no-op, VERSION list."""
 import io
 import json
 import os
+import shutil
 import subprocess
+import tempfile
 
 import pytest
 
@@ -24,7 +26,18 @@ def binary():
 
 
 @pytest.fixture()
-def server(tmp_path):
+def sockdir():
+    """A short directory for the unix sockets: sun_path holds 107 bytes, and pytest's tmp_path
+    (under the user's temporary directory) can be longer than that on its own."""
+    d = tempfile.mkdtemp(prefix="cni", dir="/tmp")
+    try:
+        yield d
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture()
+def server(sockdir):
     seen = []
 
     def add(req):
@@ -39,7 +52,7 @@ def server(tmp_path):
         seen.append(("DEL", req.container_id, req.ifname, req.pod_namespace, req.pod_name, None))
         return {"ignored": True}
 
-    sock = str(tmp_path / "run" / "dpu-cni" / "dpu-cni-server.sock")
+    sock = os.path.join(sockdir, "run", "dpu-cni", "dpu-cni-server.sock")
     srv = Server(add, dele, socket_path=sock).start()
     try:
         yield sock, seen
@@ -82,7 +95,7 @@ def test_del_check_version(binary, server):
 
 
 @pytest.mark.parametrize("case", ["daemon_error", "bad_config", "no_daemon", "bad_command", "missing_args"])
-def test_errors_match_python_shim(binary, server, tmp_path, case):
+def test_errors_match_python_shim(binary, server, sockdir, case):
     sock, _ = server
     kw, conf, cmd = {}, CONF, "ADD"
     if case == "daemon_error":
@@ -90,7 +103,7 @@ def test_errors_match_python_shim(binary, server, tmp_path, case):
     elif case == "bad_config":
         conf = b"{not json"
     elif case == "no_daemon":
-        sock = str(tmp_path / "nothing.sock")
+        sock = os.path.join(sockdir, "nothing.sock")
     elif case == "bad_command":
         cmd = "FROB"
     elif case == "missing_args":

@@ -309,7 +309,7 @@ def test_bench_multirank_rehearsal_on_one_gpu(mode, n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", str(n), "--steps", "2",
            "--warmup", "1", "--batch", str(1 << 16), "--flows", str(1 << 16), "--rehearse", "--mode", mode,
-           "--remote-frac", "0.05", "--no-variants"]
+           "--remote-frac", "0.05", "--full", "--no-variants"]
     r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, "\n".join(ln for ln in r.stderr.splitlines() if ln.startswith("[rank0]"))[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

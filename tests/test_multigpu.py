@@ -63,7 +63,7 @@ def test_rccl_all_to_all_2ranks(tmp_path):
 def test_bench_rss_two_gpus():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "5",
-           "--warmup", "2", "--batch", str(1 << 18), "--flows", str(1 << 17), "--no-variants"]
+           "--warmup", "2", "--batch", str(1 << 18), "--flows", str(1 << 17), "--full", "--no-variants"]
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
