@@ -149,6 +149,20 @@ EspBatch esp_from(const py::dict& d) {
   return a;
 }
 
+// Policer buffers (police.h PoliceArgs) from a dict of addresses.
+PoliceArgs police_from(const py::dict& d, uint64_t now_ns, bool count) {
+  PoliceArgs a{};
+  a.port_meter = ptr<const uint16_t>(d, "port_meter");
+  a.cfg = ptr<const MeterCfg>(d, "cfg");
+  a.state = ptr<MeterState>(d, "state");
+  a.meter_ctr = ptr<unsigned long long>(d, "ctr");
+  a.ws = ptr<unsigned long long>(d, "ws");
+  a.now_ns = now_ns;
+  a.count = count ? 1u : 0u;
+  if (!a.port_meter || !a.cfg || !a.state) throw std::invalid_argument("police: meter buffers missing");
+  return a;
+}
+
 void check(hipError_t e, const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
@@ -479,6 +493,46 @@ PYBIND11_MODULE(_nfdp, m) {
     check(launch_pair_fix(reinterpret_cast<const uint32_t*>(inmeta), reinterpret_cast<uint32_t*>(out_meta), n,
                           reinterpret_cast<unsigned long long*>(drop_ctr), count, reinterpret_cast<hipStream_t>(stream)),
           "launch_pair_fix");
+  });
+  // Token-bucket policer (police.h).  `meters`: {port_meter, cfg, state, ctr, ws} buffer addresses.
+  m.attr("MAX_METERS") = kMaxMeters;
+  m.attr("POLICE_MARK") = kPoliceMark;
+  m.attr("POLICE_WS_WORDS") = police_ws_words();
+  m.attr("METER_MAX_RATE") = kMeterMaxRate;
+  m.attr("METER_MAX_BURST") = kMeterMaxBurst;
+  m.def("police_ranges", [](uint32_t n) {
+    uint32_t g = 0, r = kPoliceRangeAlign;
+    if (n) police_ranges(n, g, r);
+    return py::make_tuple(g, r);
+  }, "(workgroups, slots per workgroup range) of a police launch over n slots");
+  // `phases` is for tools/police_bench.py alone (it times the kernels one by one, all four in order
+  // within one batch): nothing else may pass anything but 15, since a partial launch leaves the
+  // meters refilled but not charged, or the batch marked against stale sums.
+  m.def("launch_police", [](py::dict meters, uintptr_t inmeta, uint32_t n, uint64_t now_ns, bool count, uintptr_t stream,
+                            uint32_t phases) {
+    const PoliceArgs a = police_from(meters, now_ns, count);
+    if (!a.ws) throw std::invalid_argument("launch_police: workspace missing");
+    check(launch_police(reinterpret_cast<uint32_t*>(inmeta), n, a, reinterpret_cast<hipStream_t>(stream), phases),
+          "launch_police");
+  }, py::arg("meters"), py::arg("inmeta"), py::arg("n"), py::arg("now_ns"), py::arg("count"), py::arg("stream"),
+     py::arg("phases") = 15u);
+  m.def("launch_police_fix", [](uintptr_t inmeta, uintptr_t out_meta, uint32_t n, uintptr_t drop_ctr, bool count,
+                                uintptr_t stream) {
+    check(launch_police_fix(reinterpret_cast<uint32_t*>(inmeta), reinterpret_cast<uint32_t*>(out_meta), n,
+                            reinterpret_cast<unsigned long long*>(drop_ctr), count, reinterpret_cast<hipStream_t>(stream)),
+          "launch_police_fix");
+  });
+  m.def("oracle_police", [](py::dict meters, uintptr_t inmeta, uint32_t n, uint64_t now_ns, bool count) {
+    const PoliceArgs a = police_from(meters, now_ns, count);
+    if (n && !inmeta) throw std::invalid_argument("oracle_police: null batch");
+    py::gil_scoped_release nogil;
+    oracle_police(reinterpret_cast<uint32_t*>(inmeta), n, a);
+  });
+  m.def("oracle_police_fix", [](uintptr_t inmeta, uintptr_t out_meta, uint32_t n, uintptr_t drop_ctr, bool count) {
+    if (n && (!inmeta || !out_meta)) throw std::invalid_argument("oracle_police_fix: null batch");
+    py::gil_scoped_release nogil;
+    oracle_police_fix(reinterpret_cast<uint32_t*>(inmeta), reinterpret_cast<uint32_t*>(out_meta), n,
+                      reinterpret_cast<uint64_t*>(drop_ctr), count);
   });
   m.def("launch_steer", [](uintptr_t pkts, uintptr_t inmeta, uintptr_t list, uintptr_t list_cnt, uint32_t cap_list,
                            uint32_t cnt_len, uintptr_t send, uintptr_t pcnt, uint32_t nranks, uint32_t cap,

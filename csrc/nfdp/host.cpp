@@ -460,6 +460,44 @@ void oracle_run(const TablesView& t, const uint32_t* pkts, const uint32_t* inmet
   }
 }
 
+void oracle_police(uint32_t* inmeta, uint32_t n, const PoliceArgs& a) {
+  uint64_t allow[kMaxMeters], sum[kMaxMeters] = {}, green[kMaxMeters] = {};
+  for (int m = 0; m < kMaxMeters; ++m) {
+    allow[m] = 0;
+    if (!a.cfg[m].rate_Bps) continue;
+    meter_refill(a.cfg[m], a.state[m], a.now_ns);
+    allow[m] = meter_allow(a.state[m]);
+  }
+  const bool count = a.count && a.meter_ctr;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t im = inmeta[i], len = im >> 16;
+    const int m = police_meter_of(a.port_meter, im);
+    if (m < 0) continue;
+    sum[m] += len;   // red frames count too: the gate stays shut for the rest of the batch
+    const bool ok = sum[m] <= allow[m];
+    if (ok) green[m] += len;
+    else inmeta[i] = police_mark(im);
+    if (count) {
+      a.meter_ctr[4 * m + (ok ? 0 : 2)] += 1;
+      a.meter_ctr[4 * m + (ok ? 1 : 3)] += len;
+    }
+  }
+  for (int m = 0; m < kMaxMeters; ++m)
+    if (a.cfg[m].rate_Bps && green[m]) meter_charge(a.state[m], green[m]);
+}
+
+void oracle_police_fix(uint32_t* inmeta, uint32_t* out_meta, uint32_t n, uint64_t* drop_ctr, bool count) {
+  uint64_t c = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t im = inmeta[i];
+    if (!police_marked(im)) continue;
+    inmeta[i] = police_unmark(im);
+    out_meta[i] = make_meta(kPortNone, im >> 16, kOverflow);
+    ++c;
+  }
+  if (count && drop_ctr) { drop_ctr[kBadPort] -= c; drop_ctr[kOverflow] += c; }
+}
+
 void oracle_resume(const TablesView& t, const uint32_t* hdr, const HopState* state, uint32_t n, uint32_t* out,
                    uint32_t* out_meta, HopState* out_state, uint64_t* port_ctr, uint64_t* drop_ctr) {
   const DirectTables ta{t};

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "pipeline.h"
+#include "police.h"
 
 namespace nfdp {
 
@@ -188,6 +189,17 @@ hipError_t launch_pairs(void* pkts, uint32_t* inmeta, uint32_t n, const TablesVi
 // ... and afterwards: continuation slots' metas -> kCont with the pair's strip / hv (pair_fix_kernel)
 hipError_t launch_pair_fix(const uint32_t* inmeta, uint32_t* out_meta, uint32_t n, unsigned long long* drop_ctr,
                            bool count, hipStream_t s);
+// Token-bucket policer on ingress vports (police.h: the contract).  oracle_police judges a batch
+// at a.now_ns sequentially (refill, verdicts in slot order, red in-metas marked, meter counters,
+// tokens charged); oracle_police_fix, after oracle_run, restores the red slots' in-metas, makes
+// their out metas overflow drops and moves their count from bad_port to overflow.  GPU twins
+// (police.hip): launch_police / launch_police_fix, n up to 2^31 - 1 slots per call.
+void oracle_police(uint32_t* inmeta, uint32_t n, const PoliceArgs& a);
+void oracle_police_fix(uint32_t* inmeta, uint32_t* out_meta, uint32_t n, uint64_t* drop_ctr, bool count);
+// `phases`: which of {1: sum, 2: scan, 4: apply, 8: commit} to launch (tools/police_bench.py times them one by one)
+hipError_t launch_police(uint32_t* inmeta, uint32_t n, const PoliceArgs& a, hipStream_t s, uint32_t phases = 15u);
+hipError_t launch_police_fix(uint32_t* inmeta, uint32_t* out_meta, uint32_t n, unsigned long long* drop_ctr,
+                             bool count, hipStream_t s);
 hipError_t launch_stamp(unsigned long long* dst, hipStream_t s);
 hipError_t launch_bucket_update(const uint32_t* idx, uint32_t nb, const void* rows, void* flows,
                                 uint32_t bucket_mask, hipStream_t s);

@@ -62,7 +62,8 @@ enum Reason : uint32_t {
   kMalformed = 9,
   kRemote = 10,    // not a drop: handed to the egress GPU over xGMI (multi-GPU path), or the rest of
                    // its chain runs on another GPU (kHopXfer: port = that GPU's plane, len = frame length)
-  kOverflow = 11,  // exchange segment full (multi-GPU path)
+  kOverflow = 11,  // no capacity: exchange segment full (multi-GPU path), or port meter exceeded
+                   // (police.h; the per-meter counters tell the two apart)
   kArpTrap = 12,   // ARP copy trapped to the slow path (P4 always_trap_arp_table)
   kRecirc = 13,    // tunnel terminated: recirculate frame[len - olen:] with in_port = meta port (decap)
   kRecirc6 = 14,   // IPv6-underlay VXLAN / GENEVE to the local VTEP: the VNI lies past the header slot, so

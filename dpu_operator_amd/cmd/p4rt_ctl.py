@@ -5,7 +5,8 @@ get-pipe, add-entry, mod-entry, del-entry, dump-entries; `-g host:port` selects 
 (default 127.0.0.1:9559).  Entry syntax is the reference's: `field=value[/mask],...,priority=N,
 action=ctrl.action(arg,...)`; keys for del-entry omit the action.  Failures print the P4Runtime
 code (ALREADY_EXISTS, NOT_FOUND, INVALID_ARGUMENT, ...) on stdout and stderr and exit 1.
-Packet-IO and meter commands of the IPU tool have no MI355X pipeline counterpart.
+Packet-IO and meter commands of the IPU tool are not offered: the pipeline's only meters are the
+per-vport max_tx_rate policers (dataplane/tables.py MeterTable), set through the VSP, not P4Runtime.
 """
 from __future__ import annotations
 

@@ -82,6 +82,7 @@ class DataPlane:
         self.terms6 = T.Term6Table()     # host side: finished by resolve_recirc6 on the whole frame
         self._ipsec = None               # ESP engine (dataplane/ipsec.py), created on first use
         self.acl = T.AclTable()
+        self.meters = T.MeterTable()     # ingress policer (max_tx_rate): run() polices when a port is bound
         self.flows = T.FlowTable(flow_buckets, rss_key)
         # IPv6 flows: folded FlowKey -> the 8 raw address words of its side entry (TablesView
         # flow6_on: the device flow buffer carries the side array after the buckets)
@@ -93,6 +94,7 @@ class DataPlane:
         self.acl_mode = ACL_MODES[acl_mode]
         self._dev: dict[str, object] = {}
         self._versions: dict[str, int] = {}
+        self._police_on = False          # the committed port -> meter map binds some port
         self._acl_tiles = 1
         self.count_flows = True  # per-flow packed counters (one 64-bit atomic per packet)
         self.MAX_LAUNCH = 1 << 24
@@ -234,6 +236,8 @@ class DataPlane:
         if len(self.routes) and (self._versions.get("routes") != self.routes.version or "lpm24" not in self._dev):
             return False
         if len(self.routes6) and (self._versions.get("routes6") != self.routes6.version or "lpm6" not in self._dev):
+            return False
+        if self._versions.get("meters", 0) != self.meters.version:
             return False
         return self._versions.get("acl") == self.acl.version
 
@@ -473,6 +477,8 @@ class DataPlane:
                 self._acl6_tiles = int(t6)
             self._versions["acl"] = self.acl.version
             sent["acl"] = n
+        if self._versions.get("meters", 0) != self.meters.version or (full and "meter_cfg" in self._dev):
+            sent["meters"] = self._commit_meters()
         ft = self.flows.t
         if full or "flows" not in self._dev or self._flow6_full:
             self.harvest()
@@ -497,6 +503,51 @@ class DataPlane:
                     self._push_buckets(np.union1d(dirty, self._flow_lag), "flows_b")
                     self._flow_lag = np.zeros(0, np.int64)
         return sent
+
+    def _commit_meters(self) -> int:
+        """Policer tables (csrc/nfdp/police.h) to the device: the meters' configuration and the
+        port map, and the state rows of new / re-configured meters only (a full bucket), so every
+        other meter keeps its tokens across commits.  Returns the number of meters reset."""
+        m = self.meters
+        self._buf("meter_cfg", m.a)
+        self._buf("port_meter", m.port_meter)
+        if "meter_state" not in self._dev:
+            self._zeros("meter_state", 2 * T.MAX_METERS)
+            self._zeros("meter_ctr", 4 * T.MAX_METERS)
+            if self.gpu:
+                self._zeros("meter_ws", int(self.nf.POLICE_WS_WORDS))   # range sums / bases, allow, green
+        changed = m.take_changed()
+        if changed:
+            rows = m.full_state(changed).view(np.uint64).reshape(-1, 2)
+            if self.gpu:
+                torch = _torch()
+                idx = torch.as_tensor(changed, dtype=torch.int64, device=self.tdev)
+                self._dev["meter_state"].view(-1, 2)[idx] = torch.from_numpy(rows.view(np.int64)).to(self.tdev)
+            else:
+                self._dev["meter_state"].reshape(-1, 2)[changed] = rows
+        self._versions["meters"] = m.version
+        self._police_on = m.active()   # (as committed: run() polices when some port is bound)
+        return len(changed)
+
+    def _meter_ptrs(self) -> dict:
+        return {"port_meter": self._ptr("port_meter"), "cfg": self._ptr("meter_cfg"), "state": self._ptr("meter_state"),
+                "ctr": self._ptr("meter_ctr"), "ws": self._ptr("meter_ws")}
+
+    def meter_state(self) -> np.ndarray:
+        """[MAX_METERS, 2] uint64 = tokens (1e-9 byte), last refill (ns)."""
+        raw = self._dev.get("meter_state")
+        if raw is None:
+            return np.zeros((T.MAX_METERS, 2), np.uint64)
+        raw = raw.cpu().numpy().view(np.uint64) if self.gpu else raw
+        return raw.reshape(-1, 2).copy()
+
+    def meter_counters(self) -> np.ndarray:
+        """[MAX_METERS, 4] uint64 = green_pkts, green_bytes, red_pkts, red_bytes."""
+        raw = self._dev.get("meter_ctr")
+        if raw is None:
+            return np.zeros((T.MAX_METERS, 4), np.uint64)
+        raw = raw.cpu().numpy().view(np.uint64) if self.gpu else raw
+        return raw.reshape(-1, 4).copy()
 
     def _push_buckets(self, dirty: np.ndarray, dst: str = "flows") -> None:
         ft = self.flows.t
@@ -690,20 +741,27 @@ class DataPlane:
         return out, meta, lat
 
     def run(self, pkts, inmeta, out=None, meta=None, lat=None, stamp: bool = True, stream=None,
-            flags: int = 0) -> BatchResult:
+            flags: int = 0, now_ns: int | None = None) -> BatchResult:
         """Process one batch.  GPU: pkts/inmeta torch tensors on the device ([n,64] uint8 / [n]
-        int32); CPU: numpy arrays (runs the C++ oracle)."""
+        int32); CPU: numpy arrays (runs the C++ oracle).  With a port bound to a meter the batch is
+        policed (csrc/nfdp/police.h) at its arrival time `now_ns` (None: time.monotonic_ns()): the
+        police pass marks red frames in `inmeta` before the pipeline, the fix pass restores them."""
         n = int(pkts.shape[0])
         if TRACER.enabled:
             with TRACER.span("dataplane.run", n=n, gpu=self.gpu):
-                return self._run(pkts, inmeta, out, meta, lat, stamp, stream, flags)
-        return self._run(pkts, inmeta, out, meta, lat, stamp, stream, flags)
+                return self._run(pkts, inmeta, out, meta, lat, stamp, stream, flags, now_ns)
+        return self._run(pkts, inmeta, out, meta, lat, stamp, stream, flags, now_ns)
 
-    def _run(self, pkts, inmeta, out, meta, lat, stamp, stream, flags) -> BatchResult:
+    def _run(self, pkts, inmeta, out, meta, lat, stamp, stream, flags, now_ns=None) -> BatchResult:
         n = int(pkts.shape[0])
         if out is None:
             out, meta, lat = self.alloc_batch(n)
         tp = self.tables_ptrs()
+        police = self._police_on
+        if police:
+            if n > 0x7FFFFFFF:
+                raise ValueError("a policed batch holds at most 2^31 - 1 slots")
+            now_ns = time.monotonic_ns() if now_ns is None else int(now_ns)
         if self.gpu:
             torch = _torch()
             if pkts.device != self.tdev or inmeta.device != self.tdev:
@@ -726,6 +784,9 @@ class DataPlane:
                 self.nf.launch_stamp(t0_ptr, s)
             elif stamp:
                 t0_ptr = 0
+            if police:
+                # before the pair pass: a policed head of a wide pair is not terminated
+                self.nf.launch_police(self._meter_ptrs(), inmeta.data_ptr(), n, now_ns, not (flags & 1), s)
             if pairs:
                 # wide header pairs resolved in place over the whole batch first (kernels.hip pair_kernel)
                 self.nf.launch_pairs(tp, pkts.data_ptr(), inmeta.data_ptr(), n, self._ptr("port_ctr"),
@@ -754,6 +815,9 @@ class DataPlane:
                 )
             if pairs:   # continuation slots: kCont metas carrying their pair's strip / valid bytes
                 self.nf.launch_pair_fix(inmeta.data_ptr(), meta.data_ptr(), n, self._ptr("drop_ctr"), not (flags & 1), s)
+            if police:  # red slots: in-meta restored, meta -> overflow drop, bad_port count -> overflow
+                self.nf.launch_police_fix(inmeta.data_ptr(), meta.data_ptr(), n, self._ptr("drop_ctr"),
+                                          not (flags & 1), s)
             if side is not None:
                 self._apply_learn(s)
             ex = {"lat": lat}
@@ -766,9 +830,15 @@ class DataPlane:
         acl = np.zeros(n, np.int32)
         side = self._side_buffers(n) if self.side_active() else None
         hop = np.zeros((n, 8), np.uint32) if self.chains.split() else None
+        if police:
+            self.nf.oracle_police(self._meter_ptrs(), im.ctypes.data, n, now_ns, not (flags & 1))
         self.nf.oracle_run(tp, pk.ctypes.data, im.ctypes.data, n, out.ctypes.data, meta.ctypes.data,
                            self._ptr("flow_ctr"), self._ptr("port_ctr"), self._ptr("drop_ctr"),
                            hashes.ctypes.data, acl.ctypes.data, side, hop_state=hop.ctypes.data if hop is not None else 0)
+        if police:
+            # (oracle_run takes no flags and always counts its drops: the red slots' bad_port
+            # counts are there to be moved, whatever flags says)
+            self.nf.oracle_police_fix(im.ctypes.data, meta.ctypes.data, n, self._ptr("drop_ctr"), True)
         if side is not None:
             self._apply_learn()
         ex = {"hash": hashes, "acl": acl}
@@ -908,6 +978,8 @@ class DataPlane:
     def reset_counters(self) -> None:
         self._alloc_counters()
         self.flow_totals[:] = 0
+        if "meter_ctr" in self._dev:   # the meters' counters, not their state
+            self._zeros("meter_ctr", 4 * T.MAX_METERS)
 
 
 class GraphedRun:
@@ -939,6 +1011,7 @@ class GraphedRun:
         torch = _torch()
         dp = self.dp
         dp.commit()
+        self._refuse_meters()
         s = torch.cuda.Stream(dp.tdev)
         s.wait_stream(torch.cuda.current_stream(dp.tdev))
         with torch.cuda.stream(s):       # warm-up: one-time kernel attributes, side buffers
@@ -952,7 +1025,14 @@ class GraphedRun:
         self.gen = dp._gen
         self.captures += 1
 
+    def _refuse_meters(self) -> None:
+        # a captured graph would replay one arrival time: refused rather than silently not enforced
+        if self.dp.meters.active() or self.dp._police_on:
+            raise NotImplementedError("a captured graph does not police: a port is bound to a meter "
+                                      "(use DataPlane.run)")
+
     def __call__(self, pkts=None, inmeta=None) -> BatchResult:
+        self._refuse_meters()
         if self.dp._gen != self.gen:
             self._capture()
         if pkts is not None:

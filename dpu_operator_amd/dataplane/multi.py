@@ -189,8 +189,15 @@ class MultiDataPlane:
         plane), and resume when every plane has its new tables."""
         from .engine import commit_guard
 
+        self._refuse_meters()
         with commit_guard(self.planes):
             return self._commit_all(full)
+
+    def _refuse_meters(self) -> None:
+        # a meter's frames would spread over the planes, each with a bucket of its own: refused
+        # rather than silently not enforced
+        if any(p.meters.active() for p in self.planes):
+            raise NotImplementedError("the multi-GPU planes do not police: a port is bound to a meter")
 
     def _commit_all(self, full: bool) -> dict:
         # learned MACs of every GPU reach the shared model before it is re-uploaded anywhere
@@ -307,6 +314,7 @@ class MultiDataPlane:
         comes out of its first GPU with meta REMOTE (port = the GPU plane) and a HopState record;
         its header slot and record go device-to-device to that plane (the xGMI hop), which runs the
         rest of the chain (DataPlane.resume), as often as the chain hands it on."""
+        self._refuse_meters()
         if self.gpu:
             import torch
 

@@ -56,7 +56,8 @@ HOP_NAMES = {
     "vlan": HOP_VLAN, "drop": HOP_DROP, "punt": HOP_PUNT, "route": HOP_ROUTE,
 }
 
-# reasons (nfdp.h Reason)
+# reasons (nfdp.h Reason).  overflow = no capacity: exchange segment full, or port meter exceeded
+# (the per-meter counters, DataPlane.meter_counters(), tell the two apart)
 REASONS = {
     0: "ok", 1: "bad_port", 2: "vlan_drop", 3: "spoof", 4: "acl_deny", 5: "no_route",
     6: "too_big", 7: "chain_drop", 8: "ttl_expired", 9: "malformed", 10: "remote", 11: "overflow",
@@ -281,6 +282,101 @@ class PortTable:
 
     def mirror_port(self, idx: int) -> int | None:
         return int(self.a[idx]["ext"]) >> 16 if self.a[idx]["flags"] & PORT_MIRROR else None
+
+
+MAX_METERS = 256                 # police.h kMaxMeters
+MAX_FRAME = 9600                 # nfdp.h kMaxFrame
+POLICE_MARK = 0xE000             # police.h kPoliceMark: in-meta port of a red frame = POLICE_MARK | port
+METER_MAX_MBPS = 400000
+METER_MAX_BURST = (1 << 31) - 1
+METER_NANO = 10 ** 9             # token unit: 1e-9 byte
+METER_CFG_DTYPE = np.dtype([("rate_Bps", "<u8"), ("burst_bytes", "<u8"), ("full_ns", "<u8"), ("pad", "<u8")])
+METER_STATE_DTYPE = np.dtype([("tokens", "<u8"), ("last_ns", "<u8")])
+assert METER_CFG_DTYPE.itemsize == 32 and METER_STATE_DTYPE.itemsize == 16
+
+
+class MeterTable:
+    """Token-bucket meters of the ingress policer (csrc/nfdp/police.h): what enforces a VF's
+    ``max_tx_rate`` (the reference leaves it to the NIC, dpu-cni/pkgs/sriov/sriov.go LinkSetVfRate).
+    ``a``: the meters' configuration, ``port_meter``: port -> meter id + 1 (0 = unmetered; ports may
+    share a meter).  The state (tokens, last refill) lives with the data plane; ``take_changed()``
+    names the meters whose state the next commit resets to a full bucket."""
+
+    def __init__(self):
+        self.a = np.zeros(MAX_METERS, METER_CFG_DTYPE)
+        self.port_meter = np.zeros(MAX_PORTS, np.uint16)
+        self.version = 0
+        self._changed: set[int] = set()
+
+    @staticmethod
+    def default_burst(rate_Bps: int) -> int:
+        """The bytes sent in 10 ms at the rate, at least two maximum frames (so a maximum frame
+        always fits a full bucket)."""
+        return min(max(rate_Bps // 100, 2 * MAX_FRAME), METER_MAX_BURST)
+
+    def _check(self, meter: int) -> None:
+        if not 0 <= meter < MAX_METERS:
+            raise ValueError(f"meter {meter} out of range (0..{MAX_METERS - 1})")
+
+    def set(self, meter: int, mbps: int, burst_bytes: int | None = None) -> None:
+        """Configure a meter: `mbps` as `ip link set ... max_tx_rate` (Mbit/s), `burst_bytes` the
+        bucket depth.  A meter whose configuration changes starts over with a full bucket."""
+        self._check(meter)
+        if not 1 <= int(mbps) <= METER_MAX_MBPS:
+            raise ValueError(f"meter rate {mbps} Mbit/s out of range (1..{METER_MAX_MBPS})")
+        rate = int(mbps) * 125000
+        burst = self.default_burst(rate) if burst_bytes is None else int(burst_bytes)
+        if not 1 <= burst <= METER_MAX_BURST:
+            raise ValueError(f"meter burst {burst} B out of range (1..{METER_MAX_BURST})")
+        new = (rate, burst, -(-burst * METER_NANO // rate), 0)
+        if tuple(int(x) for x in self.a[meter]) == new:
+            return
+        self.a[meter] = new
+        self._changed.add(meter)
+        self.version += 1
+
+    def clear(self, meter: int) -> None:
+        """Remove a meter; the ports bound to it become unmetered."""
+        self._check(meter)
+        self.a[meter] = np.zeros((), METER_CFG_DTYPE)
+        self.port_meter[self.port_meter == meter + 1] = 0
+        self._changed.add(meter)
+        self.version += 1
+
+    def bind(self, port: int, meter: int | None) -> None:
+        """Police what enters on `port` with `meter` (None: unmetered)."""
+        if not 0 <= port < MAX_PORT_ID:
+            raise ValueError(f"port index {port} out of range")
+        if meter is not None:
+            self._check(meter)
+            if not self.configured(meter):
+                raise ValueError(f"meter {meter} is not configured")
+        v = 0 if meter is None else meter + 1
+        if int(self.port_meter[port]) != v:
+            self.port_meter[port] = v
+            self.version += 1
+
+    def configured(self, meter: int) -> bool:
+        return bool(self.a[meter]["rate_Bps"])
+
+    def meter_of(self, port: int) -> int | None:
+        v = int(self.port_meter[port])
+        return v - 1 if v else None
+
+    def active(self) -> bool:
+        """Some port is bound to a meter: batches are policed."""
+        return bool(self.port_meter.any())
+
+    def take_changed(self) -> list[int]:
+        out = sorted(self._changed)
+        self._changed.clear()
+        return out
+
+    def full_state(self, meters) -> np.ndarray:
+        """State rows of new / re-configured meters: a full bucket, never refilled yet."""
+        st = np.zeros(len(meters), METER_STATE_DTYPE)
+        st["tokens"] = self.a["burst_bytes"][list(meters)] * np.uint64(METER_NANO)
+        return st
 
 
 class RouteTable:

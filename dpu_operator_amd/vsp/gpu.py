@@ -14,6 +14,8 @@ It implements the same four services as the reference's VSPs, but instead of pro
       NF-out, dst=VF MAC -> NF-out      (K13  hairpin, in_port action)
       NF-out -> wire, wire -> NF-out    (K11 both ways)
 * gpu-nf:// chains from the SFC reconciler -> chain-table entries (NFs run inside the kernel)
+* set_vf_rate(vf, mbps) / the VF's max_tx_rate in netlink -> a token-bucket meter on the VF port
+  (meter id = vf; dataplane/tables.py MeterTable, csrc/nfdp/police.h), enforced by DataPlane.run
 
 Ports: vport i = data-plane port i; the uplink ("wire", the RPM/SFP port of the reference's VSPs)
 is port 4000.  All mutations happen under the VSP lock and are committed atomically per RPC.
@@ -68,7 +70,7 @@ NF_BRIDGE_BASE = 100
 _MUTATING = {"SetNumVfs": "set_num_vfs", "CreateBridgePort": "create_bridge_port",
              "DeleteBridgePort": "delete_bridge_port", "CreateNetworkFunction": "create_network_function",
              "DeleteNetworkFunction": "delete_network_function", "Init": "init", "GpuChain": "on_gpu_chain",
-             "InstallFlows": "_install_flows_rec"}
+             "InstallFlows": "_install_flows_rec", "SetVfRate": "set_vf_rate"}
 # installs up to this many flows are journaled record-by-record; bigger bulk loads checkpoint
 JOURNAL_FLOWS_MAX = 4096
 
@@ -163,6 +165,7 @@ class GpuVsp(VspBase):
         self._uplink_vp = None                  # the resolved wire vport (closed with the live path)
         self.port_state: dict[int, tuple[bool, bool, int]] = {}  # port -> (link, rx, mtu) from the agent
         self.agent_bridge = None
+        self._rate_warned = False
         self.journal = Journal(state_dir, "gpu-vsp") if state_dir else None
         self._replaying = False
         self.restored = 0
@@ -227,7 +230,85 @@ class GpuVsp(VspBase):
         else:
             dp.ports.set(i, flags=T.PORT_VALID, bridge_id=VF_BRIDGE, mac=v["mac"], peer_mac=v["mac"],
                          default_out=WIRE_PORT)
+        self._apply_rate(i)
         self._apply_port_state(i)
+
+    # ------------------------------------------------------------------ max_tx_rate
+    def _rate_enforced(self) -> bool:
+        """DataPlane.run polices (the batch engine, process()); the resident ring, the native I/O
+        engine and the multi-GPU planes do not yet."""
+        return not hasattr(self.dp, "planes") and not (self.live and self.live_engine in ("ring", "native"))
+
+    def _apply_rate(self, i: int) -> None:
+        """The vport's max_tx_rate as meter `i` on port `i` (0: no meter)."""
+        v, meters = self.vports[i], self.dp.meters
+        rate = int(v.get("max_tx_rate") or 0)
+        if rate and i < T.MAX_METERS and not self._rate_enforced():
+            if not self._rate_warned:
+                self._rate_warned = True
+                log.warning("max_tx_rate is stored but not enforced with live_engine=%s / %d GPU(s) yet",
+                            self.live_engine, self.gpus)
+            rate = 0
+        if rate and i < T.MAX_METERS:
+            meters.set(i, rate, v.get("burst_bytes"))
+            meters.bind(i, i)
+        elif i < T.MAX_METERS and (meters.meter_of(i) is not None or meters.configured(i)):
+            meters.clear(i)
+
+    def set_vf_rate(self, vf: int, max_tx_rate_mbps: int, burst_bytes: int | None = None) -> None:
+        """`ip link set <pf> vf <vf> max_tx_rate <mbps>` for a GPU vport: what the VF transmits is
+        policed to the rate (0 = off) with a bucket of `burst_bytes` (default: 10 ms at the rate)."""
+        vf, rate = int(vf), int(max_tx_rate_mbps)
+        with self._lock:
+            self._ensure_dp()
+            if vf not in self.vports:
+                raise ValueError(f"VF {vf} does not exist (SetNumVfs first)")
+            if vf >= T.MAX_METERS:
+                raise ValueError(f"max_tx_rate is available on VFs 0..{T.MAX_METERS - 1}")
+            if not 0 <= rate <= T.METER_MAX_MBPS:
+                raise ValueError(f"max_tx_rate {rate} Mbit/s out of range (0..{T.METER_MAX_MBPS})")
+            if burst_bytes is not None and not 1 <= int(burst_bytes) <= T.METER_MAX_BURST:
+                raise ValueError(f"burst {burst_bytes} B out of range (1..{T.METER_MAX_BURST})")
+            self.vports[vf].update(max_tx_rate=rate, burst_bytes=None if burst_bytes is None else int(burst_bytes),
+                                   rate_src="api" if rate else None)
+            self._apply_rate(vf)
+            self._commit()
+            self._journal("SetVfRate", (vf, rate, burst_bytes))
+
+    def _netlink_vf_rate(self, pf: int, vf: int, mac: str) -> int | None:
+        """The VF's max_tx_rate in this VSP's netlink manager (the colocated case: the CNI's
+        link_set_vf went to the same manager), 0 included; None when that PF / VF is not known
+        there.  The PF is the link whose VF record `vf` carries the bridge port's MAC (the CNI sets
+        the pod MAC as the VF's admin MAC); without such a record, PF <pf> is taken to be the pf-th
+        link that has VF records, in ifindex order (an assumption: docs/DATAPLANE.md "Policer")."""
+        try:
+            pfs = sorted((l for l in self.nl.link_list() if l.vfs), key=lambda l: l.index)
+        except Exception:  # noqa: BLE001 - no netlink here: nothing known
+            return None
+        mac = (mac or "").lower()
+        for l in pfs:
+            if vf < len(l.vfs) and mac and l.vfs[vf].mac.lower() == mac:
+                return int(l.vfs[vf].max_tx_rate or 0)
+        if pf >= len(pfs) or vf >= len(pfs[pf].vfs):
+            return None
+        return int(pfs[pf].vfs[vf].max_tx_rate or 0)
+
+    def _pick_up_rate(self, pf: int, vf: int) -> None:
+        """create_bridge_port: the pod's max_tx_rate from netlink, where the VF is known there.  A
+        rate of 0 there clears a rate taken from netlink earlier (the previous pod's), never one
+        an operator set through set_vf_rate."""
+        v = self.vports[vf]
+        rate = self._netlink_vf_rate(pf, vf, v["pod_mac"])
+        if rate is None:
+            return
+        if rate and (vf >= T.MAX_METERS or rate > T.METER_MAX_MBPS):
+            log.warning("VF %d: max_tx_rate %d Mbit/s from netlink is not applied (meters exist for VFs 0..%d, "
+                        "rates up to %d Mbit/s)", vf, rate, T.MAX_METERS - 1, T.METER_MAX_MBPS)
+            rate = 0
+        if rate:
+            v.update(max_tx_rate=rate, burst_bytes=None, rate_src="netlink")
+        elif v.get("rate_src") == "netlink":
+            v.update(max_tx_rate=0, burst_bytes=None, rate_src=None)
 
     def _apply_port_state(self, i: int) -> None:
         st = self.port_state.get(i)
@@ -412,6 +493,8 @@ class GpuVsp(VspBase):
             self._program_port(i)
         for i in [i for i in self.vports if i >= n and self.vports[i]["role"] == "free"]:
             self.dp.ports.clear(i)
+            self.vports[i]["max_tx_rate"] = 0
+            self._apply_rate(i)
             del self.vports[i]
             tap = self.taps.pop(i, None)
             if tap is not None:
@@ -450,6 +533,7 @@ class GpuVsp(VspBase):
             raise ValueError(f"logical bridge / vlan {vlan} out of range 1-4094")
         v = self.vports[vf]
         v.update(role="vf", vlan=vlan, pod_mac=_mac_str(mac) if mac else v["mac"])
+        self._pick_up_rate(int(m.group(1)), vf)
         self.bridge_ports[name] = vf
         self._apply_steering()
 
@@ -459,6 +543,8 @@ class GpuVsp(VspBase):
             return
         v = self.vports[vf]
         v.update(role="free", vlan=0, pod_mac=v["mac"])
+        if v.get("rate_src") == "netlink":   # the pod's limit leaves with the pod (the CNI resets the VF too)
+            v.update(max_tx_rate=0, burst_bytes=None, rate_src=None)
         self._apply_steering()
 
     def create_network_function(self, inp: str, out: str):
@@ -574,6 +660,9 @@ class GpuVsp(VspBase):
                     if snap.get("dp_snapshot"):
                         dp = self._ensure_dp()
                         snapshot.load(dp, os.path.join(os.path.dirname(self.journal.log_path), snap["dp_snapshot"]))
+                        for i in self.vports:      # (the meters are not part of the table snapshot)
+                            self._apply_rate(i)
+                        dp.commit()
                         for name, (cid, kinds) in snap["gpu_chains"].items():
                             self.gpu_chains[name] = int(cid)
                             self.chain_kinds[name] = list(kinds)
