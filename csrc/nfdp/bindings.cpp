@@ -254,6 +254,30 @@ PYBIND11_MODULE(_nfdp, m) {
       .def("find", [](const FlowTableHost& t, py::tuple k) {
         return t.find(FlowKey{k[0].cast<uint32_t>(), k[1].cast<uint32_t>(), k[2].cast<uint32_t>(), k[3].cast<uint32_t>()});
       })
+      .def("find_many", [](const FlowTableHost& t, U32Arr keys) {
+        if (keys.ndim() != 2 || keys.shape(1) != 4) throw std::invalid_argument("find_many expects [n,4] uint32 keys");
+        auto k = keys.unchecked<2>();
+        py::array_t<int64_t> slots(keys.shape(0));
+        auto o = slots.mutable_unchecked<1>();
+        for (py::ssize_t i = 0; i < keys.shape(0); ++i) o(i) = t.find(FlowKey{k(i, 0), k(i, 1), k(i, 2), k(i, 3)});
+        return slots;
+      })
+      .def("keys_at", [](const FlowTableHost& t, py::array_t<int64_t, py::array::c_style | py::array::forcecast> idx) {
+        // [k,4] uint32: the keys of these slots without the used bit (an empty slot: zeros)
+        if (idx.ndim() != 1) throw std::invalid_argument("keys_at expects a 1-d slot index array");
+        auto& v = t.slots();
+        auto s = idx.unchecked<1>();
+        py::array_t<uint32_t> keys({idx.shape(0), (py::ssize_t)4});
+        auto o = keys.mutable_unchecked<2>();
+        for (py::ssize_t i = 0; i < idx.shape(0); ++i) {
+          if (s(i) < 0 || (size_t)s(i) >= v.size()) throw std::out_of_range("keys_at: slot out of range");
+          const FlowKey& k = v[(size_t)s(i)].key;
+          const bool used = k.meta & kSlotUsed;
+          o(i, 0) = used ? k.src_ip : 0; o(i, 1) = used ? k.dst_ip : 0; o(i, 2) = used ? k.ports : 0;
+          o(i, 3) = used ? (k.meta & ~kSlotUsed) : 0;
+        }
+        return keys;
+      })
       .def("slots", [](const FlowTableHost& t) {
         // [nbuckets*4, 8] uint32: key (4 words, meta |= 0x100 when used) + action (4 words)
         auto& v = t.slots();
@@ -930,6 +954,40 @@ PYBIND11_MODULE(_nfdp, m) {
   m.def("launch_harvest", [](uintptr_t ctr, uintptr_t out, uint32_t n, uintptr_t stream) {
     check(launch_harvest(reinterpret_cast<unsigned long long*>(ctr), reinterpret_cast<unsigned long long*>(out), n,
                          reinterpret_cast<hipStream_t>(stream)), "harvest");
+  });
+  // Flow aging (age.h).  Addresses: ctr u64[n], rows AgeRow[n], out u32[cap] (sweep) / u64[n]
+  // (harvest), count u32[1].
+  m.attr("AGE_NEW") = kAgeNew;
+  m.attr("AGE_TOUCHED") = kAgeTouched;
+  m.attr("AGE_TMO_MASK") = kAgeTmoMask;
+  m.def("age_grid", [](uint64_t n) {
+    uint32_t g = 0, per = 0;
+    age_grid(n, g, per);
+    return py::make_tuple(g, per);
+  }, "(workgroups, slots per pass) of a sweep over n slots: a thread takes a second slot from n > slots per pass");
+  m.def("launch_age_sweep", [](uintptr_t ctr, uintptr_t rows, uint64_t n, uint32_t now_tick, uintptr_t out, uint32_t cap,
+                               uintptr_t count, uintptr_t stream) {
+    check(launch_age_sweep(reinterpret_cast<const unsigned long long*>(ctr), reinterpret_cast<AgeRow*>(rows), n, now_tick,
+                           reinterpret_cast<uint32_t*>(out), cap, reinterpret_cast<uint32_t*>(count),
+                           reinterpret_cast<hipStream_t>(stream)), "launch_age_sweep");
+  });
+  m.def("launch_harvest_age", [](uintptr_t ctr, uintptr_t rows, uintptr_t out, uint64_t n, uintptr_t stream) {
+    check(launch_harvest_age(reinterpret_cast<unsigned long long*>(ctr), reinterpret_cast<AgeRow*>(rows),
+                             reinterpret_cast<unsigned long long*>(out), n, reinterpret_cast<hipStream_t>(stream)),
+          "launch_harvest_age");
+  });
+  m.def("oracle_age_sweep", [](uintptr_t ctr, uintptr_t rows, uint64_t n, uint32_t now_tick, uintptr_t out, uint32_t cap,
+                               uintptr_t count) {
+    if (!count || (n && (!ctr || !rows)) || (cap && !out)) throw std::invalid_argument("oracle_age_sweep: null buffer");
+    py::gil_scoped_release nogil;
+    oracle_age_sweep(reinterpret_cast<const uint64_t*>(ctr), reinterpret_cast<AgeRow*>(rows), n, now_tick,
+                     reinterpret_cast<uint32_t*>(out), cap, reinterpret_cast<uint32_t*>(count));
+  });
+  m.def("oracle_harvest_age", [](uintptr_t ctr, uintptr_t rows, uintptr_t out, uint64_t n) {
+    if (n && (!ctr || !rows || !out)) throw std::invalid_argument("oracle_harvest_age: null buffer");
+    py::gil_scoped_release nogil;
+    oracle_harvest_age(reinterpret_cast<uint64_t*>(ctr), reinterpret_cast<AgeRow*>(rows),
+                       reinterpret_cast<uint64_t*>(out), n);
   });
 
   // ---- native packet I/O engine (iox.h): ports, backends, engine; pod-side memif tools ----

@@ -498,6 +498,27 @@ void oracle_police_fix(uint32_t* inmeta, uint32_t* out_meta, uint32_t n, uint64_
   if (count && drop_ctr) { drop_ctr[kBadPort] -= c; drop_ctr[kOverflow] += c; }
 }
 
+void oracle_age_sweep(const uint64_t* ctr, AgeRow* rows, uint64_t n, uint32_t now_tick, uint32_t* out, uint32_t cap,
+                      uint32_t* count) {
+  uint32_t c = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (!(rows[i].tmo & kAgeTmoMask)) continue;   // (the counter of an unarmed slot is not read)
+    if (age_step(rows[i], ctr[i], now_tick) != kAgeExpired) continue;
+    if (c < cap) out[c] = (uint32_t)i;
+    ++c;
+  }
+  *count = c;
+}
+
+void oracle_harvest_age(uint64_t* ctr, AgeRow* rows, uint64_t* out, uint64_t n) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t v = ctr[i];
+    ctr[i] = 0;
+    out[i] = v;
+    age_harvest_step(rows[i], v);
+  }
+}
+
 void oracle_resume(const TablesView& t, const uint32_t* hdr, const HopState* state, uint32_t n, uint32_t* out,
                    uint32_t* out_meta, HopState* out_state, uint64_t* port_ctr, uint64_t* drop_ctr) {
   const DirectTables ta{t};

@@ -7,6 +7,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "age.h"
 #include "pipeline.h"
 #include "police.h"
 
@@ -200,6 +201,17 @@ void oracle_police_fix(uint32_t* inmeta, uint32_t* out_meta, uint32_t n, uint64_
 hipError_t launch_police(uint32_t* inmeta, uint32_t n, const PoliceArgs& a, hipStream_t s, uint32_t phases = 15u);
 hipError_t launch_police_fix(uint32_t* inmeta, uint32_t* out_meta, uint32_t n, unsigned long long* drop_ctr,
                              bool count, hipStream_t s);
+// Flow aging (age.h: the contract).  oracle_age_sweep visits the n slots in order:
+// *count = all expired slots, out = the first min(*count, cap) of them in slot order.
+// oracle_harvest_age is the age-aware read-and-reset of the packed counters.  GPU twins (age.hip):
+// launch_age_sweep (zeroes *count itself) / launch_harvest_age, n up to 2^32 - 1 slots.
+void oracle_age_sweep(const uint64_t* ctr, AgeRow* rows, uint64_t n, uint32_t now_tick, uint32_t* out, uint32_t cap,
+                      uint32_t* count);
+void oracle_harvest_age(uint64_t* ctr, AgeRow* rows, uint64_t* out, uint64_t n);
+hipError_t launch_age_sweep(const unsigned long long* ctr, AgeRow* rows, uint64_t n, uint32_t now_tick, uint32_t* out,
+                            uint32_t cap, uint32_t* count, hipStream_t s);
+hipError_t launch_harvest_age(unsigned long long* ctr, AgeRow* rows, unsigned long long* out, uint64_t n,
+                              hipStream_t s);
 hipError_t launch_stamp(unsigned long long* dst, hipStream_t s);
 hipError_t launch_bucket_update(const uint32_t* idx, uint32_t nb, const void* rows, void* flows,
                                 uint32_t bucket_mask, hipStream_t s);

@@ -154,6 +154,8 @@ def parse_args(argv=None):
                     help="native engine delivery threads per queue (0: run to completion, the rx threads deliver; "
                          "-1: node config)")
     ap.add_argument("--metrics-bind-address", default="", help="amd-gpu: data-plane /metrics address (off if empty)")
+    ap.add_argument("--flow-sweep-interval", type=float, default=0.0, metavar="SECONDS",
+                    help="amd-gpu: expire flows idle for their timeout every SECONDS (0 = off)")
     ap.add_argument("--agent-mbox", default="", help="amd-gpu: run the node control agent on this mailbox path")
     ap.add_argument("--agent-config", default="", help="agent SoC config file (default: one PF + --agent-vfs VFs)")
     ap.add_argument("--agent-vfs", type=int, default=8)
@@ -174,6 +176,8 @@ def _extras(a, vsp) -> list:
         register_dataplane(lambda: vsp.dp, "gpu0" if vsp.gpus == 1 else f"gpu0-{vsp.gpus - 1}", reg)
         vsp.metrics = MetricsServer(a.metrics_bind_address, reg).start()
         out.append(vsp.metrics)
+    if a.flow_sweep_interval > 0:
+        vsp.start_flow_sweeper(a.flow_sweep_interval)   # (stops with the VSP)
     if a.agent_mbox:
         from .. import cpagent
         from ..native import agent as native_agent

@@ -95,6 +95,7 @@ class DataPlane:
         self._dev: dict[str, object] = {}
         self._versions: dict[str, int] = {}
         self._police_on = False          # the committed port -> meter map binds some port
+        self._age_stats = None           # flow aging (csrc/nfdp/age.h): None until enable_flow_aging()
         self._acl_tiles = 1
         self.count_flows = True  # per-flow packed counters (one 64-bit atomic per packet)
         self.MAX_LAUNCH = 1 << 24
@@ -332,6 +333,8 @@ class DataPlane:
                 raise RuntimeError("live flow updates need enable_flow_flip() before the rings start")
             if moves:
                 self.harvest()  # counters of moved slots are attributed before the move
+        self._age_sync(dirty, bool(moves))
+        if flow:
             rows = np.union1d(dirty, self._flow_lag)
             self._push_buckets(rows, self._flows_key(self._flow_active ^ 1))
             sent["flow_buckets"] = int(len(dirty))
@@ -482,6 +485,7 @@ class DataPlane:
         ft = self.flows.t
         if full or "flows" not in self._dev or self._flow6_full:
             self.harvest()
+            self._age_sync(None, True)
             img = self._flow_image()
             self._buf("flows", img)
             if "flows_b" in self._dev:   # both copies current: nothing lags
@@ -498,6 +502,8 @@ class DataPlane:
                 if moves:
                     self.harvest()  # counters of moved slots are attributed before the move
                 sent["flow_buckets"] = int(len(dirty))
+            self._age_sync(dirty, bool(moves))
+            if len(dirty):
                 self._push_buckets(np.union1d(dirty, self._flow_lag) if "flows_b" in self._dev else dirty, "flows")
                 if "flows_b" in self._dev:
                     self._push_buckets(np.union1d(dirty, self._flow_lag), "flows_b")
@@ -726,6 +732,199 @@ class DataPlane:
             self.commit()
         return n
 
+    # ------------------------------------------------------------------ flow aging
+    # Per-flow idle timeouts (csrc/nfdp/age.h: the contract).  The rows live in "age_rows", one per
+    # flow slot; self.flows.age (tables.FlowAging) is the host side.  Nothing here runs, and no
+    # buffer exists, until enable_flow_aging().
+    def enable_flow_aging(self, tick_ns: int = 100_000_000, max_expired: int = 65536) -> None:
+        """Turn per-flow idle timeouts on: allocates one 16-B row per flow slot, the expired-slot
+        list (`max_expired` entries) and its count.  The idle clock's epoch is now."""
+        if not self.count_flows:
+            raise ValueError("flow aging reads the per-flow counters: count_flows is off")
+        if int(max_expired) < 1:
+            raise ValueError("max_expired must be positive")
+        with self._commit_lock:
+            if self._age_stats is not None:
+                raise RuntimeError("flow aging is already enabled")
+            n = self.flows.nbuckets * 4
+            self.harvest()   # (the last plain harvest: every later one keeps the rows' view of the counters)
+            self.flows.age = T.FlowAging(n, tick_ns, time.monotonic_ns())
+            self._zeros("age_rows", 2 * n)
+            self._zeros("age_list", int(max_expired), np.uint32)
+            self._zeros("age_cnt", 1, np.uint32)
+            self._age_stats = {"expired_total": 0, "sweeps": 0, "relocated": 0, "last_sweep_us": 0.0}
+
+    def _age_guard(self) -> None:
+        if self._age_stats is not None and not self.count_flows:
+            raise ValueError("flow aging is on but count_flows is off: every aged flow would expire")
+
+    def set_flow_timeout(self, keys, idle_s) -> int:
+        """Idle timeout(s) in seconds (rounded up to ticks; 0 disarms) for one key or [n, 4] keys, a
+        scalar or one per key.  Takes effect at the next commit: the flow is (re)armed with a fresh
+        idle clock.  Returns how many of the keys are installed (the others are ignored)."""
+        ag = self._age_need()
+        keys = np.ascontiguousarray(keys, np.uint32).reshape(-1, 4)
+        idle = np.broadcast_to(np.asarray(idle_s, np.float64).reshape(-1), (len(keys),))
+        ticks = [ag.ticks(x) for x in idle]
+        with self._commit_lock:
+            found = self.flows.find_many(keys) >= 0
+            for k, t, ok in zip(map(tuple, keys.tolist()), ticks, found):
+                if ok:
+                    ag.pending[k] = t
+        return int(found.sum())
+
+    def _age_need(self) -> T.FlowAging:
+        if self._age_stats is None:
+            raise RuntimeError("flow aging is off: call enable_flow_aging() first")
+        return self.flows.age
+
+    def _age_rows2(self):
+        """The rows as [nslots, 2] 64-bit words: seen, last | tmo << 32."""
+        r = self._dev["age_rows"]
+        return r.view(-1, 2) if self.gpu else r.reshape(-1, 2)
+
+    def _age_write(self, slots: np.ndarray, rows: np.ndarray) -> None:
+        """rows (T.AGE_ROW_DTYPE) -> the device rows of `slots`."""
+        if not len(slots):
+            return
+        w = np.ascontiguousarray(rows).view(np.uint64).reshape(-1, 2)
+        if self.gpu:
+            torch = _torch()
+            idx = torch.as_tensor(np.asarray(slots, np.int64), device=self.tdev)
+            self._age_rows2()[idx] = torch.from_numpy(w.view(np.int64)).to(self.tdev)
+        else:
+            self._age_rows2()[np.asarray(slots, np.int64)] = w
+
+    def age_rows(self) -> np.ndarray:
+        """A host copy of the rows (T.AGE_ROW_DTYPE, one per flow slot)."""
+        self._age_need()
+        raw = self._dev["age_rows"]
+        raw = raw.cpu().numpy() if self.gpu else raw.copy()
+        return raw.view(T.AGE_ROW_DTYPE)
+
+    def _device_flow_keys(self, slots: np.ndarray) -> np.ndarray:
+        """[k, 4] keys (used bit stripped) the committed device flow image holds in these slots."""
+        img = self._dev[self._flows_key(self._flow_active)]
+        nw = self.flows.nbuckets * 4 * 8   # the buckets' 32-bit words (an IPv6 side array may follow)
+        if self.gpu:
+            torch = _torch()
+            idx = torch.as_tensor(np.asarray(slots, np.int64), device=self.tdev)
+            k = img[: 4 * nw].view(torch.int32).view(-1, 8)[idx, :4].cpu().numpy().view(np.uint32)
+        else:
+            k = img.view(np.uint32).reshape(-1)[:nw].reshape(-1, 8)[np.asarray(slots, np.int64), :4]
+        k = np.array(k, np.uint32, copy=True)
+        k[:, 3] &= ~np.uint32(T.SLOT_USED)
+        return k
+
+    def _age_sync(self, dirty, harvested: bool) -> None:
+        """Bring the rows in line with the flow changes of the commit under way, before the new
+        buckets are pushed: rows of erased flows are cleared, the row of a flow that a cuckoo insert
+        relocated follows it exactly, pending timeouts are armed.  The relocations are derived from
+        keys, not from take_moves()' hops (eviction order, ambiguous when two inserts chain): for
+        every armed slot of a changed bucket, the key the committed device image still holds there
+        is looked up in the host table.  `dirty`: the changed buckets (None: all of them);
+        `harvested`: the age-aware harvest ran (every `seen` is 0, so a moved row stays exact)."""
+        if self._age_stats is None:
+            return
+        ag = self.flows.age
+        erased = ag.take_erased()
+        if dirty is None:
+            cand = np.nonzero(ag.tmo)[0]
+        else:
+            slots = (np.asarray(dirty, np.int64)[:, None] * 4 + np.arange(4)).reshape(-1)
+            cand = slots[ag.tmo[slots] != 0]
+        if len(cand) and self._flows_key(self._flow_active) in self._dev:
+            keys = self._device_flow_keys(cand)
+            new = self.flows.find_many(keys)
+            if erased:   # erased, even if the key was installed again since: an unarmed row
+                new[[k in erased for k in map(tuple, keys.tolist())]] = -1
+            gone, mv = cand[new < 0], (new >= 0) & (new != cand)
+            src, dst = cand[mv], new[mv]
+            if len(src) and not harvested:
+                self.harvest()
+            if len(src) or len(gone):
+                rows2 = self._age_rows2()
+                if self.gpu:
+                    torch = _torch()
+                    dev = lambda a: torch.as_tensor(a, device=self.tdev)   # noqa: E731
+                    tmp = rows2[dev(src)].clone()
+                    rows2[dev(np.concatenate([gone, src]))] = 0
+                    rows2[dev(dst)] = tmp
+                else:
+                    tmp = rows2[src].copy()
+                    rows2[np.concatenate([gone, src])] = 0
+                    rows2[dst] = tmp
+                t = ag.tmo[src].copy()
+                ag.tmo[gone] = 0
+                ag.tmo[src] = 0
+                ag.tmo[dst] = t
+                self._age_stats["relocated"] += int(len(src))
+        if ag.pending:
+            keys = np.array(list(ag.pending), np.uint32).reshape(-1, 4)
+            ticks = np.array(list(ag.pending.values()), np.uint32)
+            ag.pending = {}
+            slots = self.flows.find_many(keys)
+            ok = slots >= 0
+            self._age_write(slots[ok], T.FlowAging.armed_rows(ticks[ok]))
+            ag.tmo[slots[ok]] = ticks[ok]
+
+    def age_flows(self, now_ns: int | None = None) -> np.ndarray:
+        """One aging sweep at `now_ns` (None: time.monotonic_ns()): commits pending changes, sweeps
+        the rows on the device, removes the expired flows (their IPv6 side entries too) and commits.
+        Returns their [k, 4] keys.  With more expired flows than `max_expired` it removes what the
+        list holds; the next call gets the rest (an expired row is left as it is)."""
+        ag = self._age_need()
+        self._age_guard()
+        now_ns = time.monotonic_ns() if now_ns is None else int(now_ns)
+        with self._commit_lock:
+            self.commit()
+            n, cap, tick = self.flows.nbuckets * 4, int(len(self._dev["age_list"])), ag.now_tick(now_ns)
+            t0 = time.perf_counter()
+            if self.gpu:
+                torch = _torch()
+                s = torch.cuda.current_stream(self.tdev)
+                self.nf.launch_age_sweep(self._ptr("flow_ctr"), self._ptr("age_rows"), n, tick, self._ptr("age_list"),
+                                         cap, self._ptr("age_cnt"), s.cuda_stream)
+                s.synchronize()
+                count = int(self._dev["age_cnt"].cpu().numpy().view(np.uint32)[0])
+                k = min(count, cap)
+                slots = self._dev["age_list"][:k].cpu().numpy().view(np.uint32).astype(np.int64)
+            else:
+                self.nf.oracle_age_sweep(self._ptr("flow_ctr"), self._ptr("age_rows"), n, tick, self._ptr("age_list"),
+                                         cap, self._ptr("age_cnt"))
+                count = int(self._dev["age_cnt"][0])
+                k = min(count, cap)
+                slots = self._dev["age_list"][:k].astype(np.int64)
+            st = self._age_stats
+            st["last_sweep_us"] = (time.perf_counter() - t0) * 1e6
+            st["sweeps"] += 1
+            st["last_count"] = count
+            if not k:
+                return np.zeros((0, 4), np.uint32)
+            keys = self.flows.keys_at(slots)
+            self.flows.erase_many(keys)
+            for key in keys[(keys[:, 3] & np.uint32(T.KEY_V6)) != 0]:
+                self.flows6.pop(tuple(int(x) for x in key), None)
+            self._age_write(slots, np.zeros(k, T.AGE_ROW_DTYPE))
+            ag.tmo[slots] = 0
+            st["expired_total"] += k
+            self.commit()
+            return keys
+
+    def flow_age_stats(self) -> dict:
+        """armed (flows with a committed idle timeout), expired_total, sweeps, relocated (rows that
+        followed a cuckoo move), last_sweep_us (launch to completion of the last sweep, wall clock)."""
+        ag = self._age_need()
+        st = self._age_stats
+        return {"armed": int(np.count_nonzero(ag.tmo)), "expired_total": st["expired_total"], "sweeps": st["sweeps"],
+                "relocated": st["relocated"], "last_sweep_us": st["last_sweep_us"]}
+
+    def flow_timeouts(self, keys) -> np.ndarray:
+        """The committed idle timeouts, in ticks, of [n, 4] keys (0: not aged or not installed)."""
+        ag = self._age_need()
+        slots = self.flows.find_many(np.ascontiguousarray(keys, np.uint32).reshape(-1, 4))
+        return np.where(slots >= 0, ag.tmo[np.maximum(slots, 0)], 0).astype(np.uint32)
+
     # ------------------------------------------------------------------ run
     def alloc_batch(self, n: int):
         """Output buffers for a batch of n packets."""
@@ -756,6 +955,7 @@ class DataPlane:
         n = int(pkts.shape[0])
         if out is None:
             out, meta, lat = self.alloc_batch(n)
+        self._age_guard()
         tp = self.tables_ptrs()
         police = self._police_on
         if police:
@@ -885,6 +1085,7 @@ class DataPlane:
 
     def capture(self, n: int) -> "GraphedRun":
         """A batch of n slots as a captured HIP graph (see GraphedRun)."""
+        self._age_guard()
         return GraphedRun(self, n)
 
     def launch(self, pkts: int, inmeta: int, n: int, out: int, meta: int, lat: int = 0, t0: int | None = None,
@@ -893,6 +1094,7 @@ class DataPlane:
         word holding the real packet count (<= n), for batches whose size only the GPU knows."""
         if not self.gpu:
             raise RuntimeError("launch() is the GPU path; use run() for the oracle")
+        self._age_guard()
         s = stream if stream is not None else _torch().cuda.current_stream(self.tdev).cuda_stream
         if not self.count_flows:
             flags |= 4
@@ -907,7 +1109,8 @@ class DataPlane:
 
     # ------------------------------------------------------------------ counters
     def harvest(self) -> None:
-        """Read-and-reset the packed per-flow counters into 64-bit host totals."""
+        """Read-and-reset the packed per-flow counters into 64-bit host totals (with flow aging on:
+        the age-aware kernel / oracle, which notes in the rows what the reset would hide)."""
         if "flow_ctr" not in self._dev:
             return
         n = self.flows.nbuckets * 4
@@ -915,8 +1118,14 @@ class DataPlane:
             torch = _torch()
             tmp = torch.empty(n, dtype=torch.int64, device=self.tdev)
             s = torch.cuda.current_stream(self.tdev).cuda_stream
-            self.nf.launch_harvest(self._ptr("flow_ctr"), tmp.data_ptr(), n, s)
+            if self._age_stats is not None:   # the age-aware twin: the rows learn what the reset hides
+                self.nf.launch_harvest_age(self._ptr("flow_ctr"), self._ptr("age_rows"), tmp.data_ptr(), n, s)
+            else:
+                self.nf.launch_harvest(self._ptr("flow_ctr"), tmp.data_ptr(), n, s)
             raw = tmp.cpu().numpy().view(np.uint64)
+        elif self._age_stats is not None:
+            raw = np.empty(n, np.uint64)
+            self.nf.oracle_harvest_age(self._ptr("flow_ctr"), self._ptr("age_rows"), raw.ctypes.data, n)
         else:
             raw = self._dev["flow_ctr"].copy()
             self._dev["flow_ctr"][:] = 0
@@ -980,6 +1189,9 @@ class DataPlane:
         self.flow_totals[:] = 0
         if "meter_ctr" in self._dev:   # the meters' counters, not their state
             self._zeros("meter_ctr", 4 * T.MAX_METERS)
+        if self._age_stats is not None:
+            # the counters the rows were compared with are gone: every armed row starts over
+            self._age_write(np.arange(len(self.flows.age.tmo)), T.FlowAging.armed_rows(self.flows.age.tmo))
 
 
 class GraphedRun:

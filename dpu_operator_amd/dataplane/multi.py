@@ -179,6 +179,12 @@ class MultiDataPlane:
                 return False
             return all(p.ctrl_ports(ports, timeout_s) for p in self.planes)
 
+    def enable_flow_aging(self, *a, **kw) -> None:
+        # with port placement a flow is replicated and idle only when idle on every plane (the
+        # sweeps' verdicts would have to be ANDed across planes): out of scope, refused
+        raise NotImplementedError("the multi-GPU planes do not age flows (DataPlane.enable_flow_aging is "
+                                  "single-device)")
+
     def commit(self, full: bool = False) -> dict:
         """Every plane's commit as one update for the engines that feed them.
 

@@ -4,7 +4,9 @@ Saves every host table model of a DataPlane (ports, chains, MAC, ACL rules, LAG,
 actions, per-flow counter totals, RSS key) into one .npz written without pickling, and restores it
 into a fresh DataPlane (CPU or GPU) followed by a full commit — a restarted VSP resumes forwarding
 with identical behaviour and counters.  Flow entries are re-inserted (bucket positions may differ;
-lookups are equivalent), counters follow their flow key.
+lookups are equivalent), counters follow their flow key.  With flow aging on (DataPlane.enable_flow_aging)
+the flows' idle timeouts are saved too (``flow_idle_ticks``, aligned with ``flow_keys``, and ``age_tick_ns``);
+a load re-enables aging and re-arms them with a fresh idle clock.
 """
 from __future__ import annotations
 
@@ -33,13 +35,20 @@ def _flows(dp) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
 
 
 def save(dp, path: str) -> dict:
+    aging = getattr(dp, "_age_stats", None) is not None
+    if aging:
+        dp.commit()   # the timeouts are kept per committed slot: nothing pending while they are read
     keys, acts, totals = _flows(dp)
+    extra = {}
+    if aging:
+        occ = (dp.flows.t.slots()[:, 3] & _USED) != 0
+        extra = {"flow_idle_ticks": dp.flows.age.tmo[occ].copy(), "age_tick_ns": np.int64(dp.flows.age.tick_ns)}
     val, msk, per, n = dp.acl.arrays()
     tmp = path + ".tmp.npz"
     np.savez(tmp, ports=dp.ports.a, chains=dp.chains.a, n_chains=np.int64(dp.chains.n), macs=dp.macs.a,
              acl_value=val[:n], acl_mask=msk[:n], acl_permit=per[:n], acl_default=np.int64(dp.acl.default_permit),
              lag=dp.lag.a, n_lag=np.int64(dp.lag.n), flow_keys=keys, flow_actions=acts, flow_totals=totals,
-             rss_key=np.frombuffer(dp.rss_key, np.uint8), flow_buckets=np.int64(dp.flows.nbuckets))
+             rss_key=np.frombuffer(dp.rss_key, np.uint8), flow_buckets=np.int64(dp.flows.nbuckets), **extra)
     os.replace(tmp, path)
     return {"flows": len(keys), "acl": int(n)}
 
@@ -79,5 +88,14 @@ def load(dp, path: str) -> dict:
                     p.flow_totals[slots[own == g]] = totals[own == g]
             else:
                 dp.flow_totals[slots] = totals
+        if "flow_idle_ticks" in z.files:
+            if not hasattr(dp, "set_flow_timeout"):
+                raise NotImplementedError("the snapshot holds flow idle timeouts: the multi-GPU planes do not age flows")
+            if dp._age_stats is None:
+                dp.enable_flow_aging(tick_ns=int(z["age_tick_ns"]))
+            ticks = z["flow_idle_ticks"].astype(np.float64) * int(z["age_tick_ns"]) / dp.flows.age.tick_ns
+            for k, t in zip(map(tuple, keys.tolist()), np.ceil(ticks).astype(np.int64)):
+                if t:   # re-armed by the commit below: a fresh idle clock
+                    dp.flows.age.pending[k] = int(min(t, T.AGE_TMO_MASK))
     dp.commit(full=True)
     return {"flows": int(len(keys)), "acl": len(dp.acl.rules)}

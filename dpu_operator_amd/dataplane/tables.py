@@ -1218,12 +1218,67 @@ class AclTable:
         return val, msk, per, n
 
 
+AGE_NEW = 0x80000000             # age.h kAgeNew: armed, not yet seen by a sweep
+AGE_TOUCHED = 0x40000000         # age.h kAgeTouched: a harvest saw traffic since the last sweep
+AGE_TMO_MASK = 0x3FFFFFFF        # age.h kAgeTmoMask: idle timeouts are 1 .. 2^30 - 1 ticks
+AGE_ROW_DTYPE = np.dtype([("seen", "<u8"), ("last", "<u4"), ("tmo", "<u4")])
+assert AGE_ROW_DTYPE.itemsize == 16
+
+
+class FlowAging:
+    """Host side of flow aging (csrc/nfdp/age.h): the tick clock, the idle timeout of every slot as
+    the device holds it (``tmo``, u32 per slot, without the flag bits), and what the next commit
+    has to bring there: ``pending`` (key -> ticks: rows to (re)arm, 0 = disarm) and ``erased`` (keys
+    erased since the last commit: their rows are cleared, also when the key came back)."""
+
+    def __init__(self, nslots: int, tick_ns: int, epoch_ns: int):
+        if int(tick_ns) < 1:
+            raise ValueError("tick_ns must be positive")
+        self.tick_ns, self.epoch_ns = int(tick_ns), int(epoch_ns)
+        self.tmo = np.zeros(nslots, np.uint32)
+        self.pending: dict[tuple, int] = {}
+        self.erased: set[tuple] = set()
+
+    def ticks(self, idle_s) -> int:
+        """Seconds -> ticks, rounded up (0 stays 0: not aged)."""
+        s = float(idle_s)
+        if s < 0 or s != s:
+            raise ValueError(f"idle timeout {idle_s!r} s is negative")
+        if s == 0:
+            return 0
+        t = -(-int(round(s * 1e9)) // self.tick_ns)
+        if not 1 <= t <= AGE_TMO_MASK:
+            raise ValueError(f"idle timeout {idle_s} s is {t} ticks: out of range (1..{AGE_TMO_MASK})")
+        return t
+
+    def now_tick(self, now_ns: int) -> int:
+        return ((int(now_ns) - self.epoch_ns) // self.tick_ns) & 0xFFFFFFFF
+
+    def forget(self, keys) -> None:
+        for k in keys:
+            self.pending.pop(k, None)
+            self.erased.add(k)
+
+    def take_erased(self) -> set:
+        out, self.erased = self.erased, set()
+        return out
+
+    @staticmethod
+    def armed_rows(ticks) -> np.ndarray:
+        """Fresh rows for these timeouts: armed with AGE_NEW (0 ticks: an all-zero, unarmed row)."""
+        t = np.asarray(ticks, np.uint32).reshape(-1)
+        rows = np.zeros(len(t), AGE_ROW_DTYPE)
+        rows["tmo"] = np.where(t != 0, t | np.uint32(AGE_NEW), np.uint32(0))
+        return rows
+
+
 class FlowTable:
     """Thin wrapper over the native authoritative cuckoo table."""
 
     def __init__(self, nbuckets: int, rss_key: bytes = RSS_KEY):
         self.t = _nfdp_mod().FlowTable(nbuckets, rss_key)
         self.rss_key = rss_key
+        self.age: FlowAging | None = None   # set by DataPlane.enable_flow_aging: erases are noted there
 
     def __len__(self) -> int:
         return len(self.t)
@@ -1239,10 +1294,24 @@ class FlowTable:
         return self.t.insert_many(np.ascontiguousarray(keys, np.uint32), np.ascontiguousarray(actions, np.uint32))
 
     def erase(self, key) -> bool:
-        return self.t.erase(tuple(int(x) for x in key))
+        k = tuple(int(x) for x in key)
+        if self.age is not None:
+            self.age.forget([k])
+        return self.t.erase(k)
 
     def erase_many(self, keys: np.ndarray) -> int:
-        return int(self.t.erase_many(np.ascontiguousarray(keys, np.uint32)))
+        keys = np.ascontiguousarray(keys, np.uint32)
+        if self.age is not None:
+            self.age.forget(map(tuple, keys.reshape(-1, 4).tolist()))
+        return int(self.t.erase_many(keys))
 
     def find(self, key) -> int:
         return self.t.find(tuple(int(x) for x in key))
+
+    def find_many(self, keys: np.ndarray) -> np.ndarray:
+        """Slots (int64, -1: not installed) of [n, 4] keys."""
+        return self.t.find_many(np.ascontiguousarray(keys, np.uint32).reshape(-1, 4))
+
+    def keys_at(self, slots) -> np.ndarray:
+        """[k, 4] keys held by these slots (without the used bit; an empty slot: zeros)."""
+        return self.t.keys_at(np.ascontiguousarray(slots, np.int64).reshape(-1))

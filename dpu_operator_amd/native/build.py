@@ -52,7 +52,8 @@ def _includes() -> list[str]:
 MODULES = {
     "_nfdp": {
         "dir": CSRC / "nfdp",
-        "sources": ["kernels.hip", "shard.hip", "pktio.hip", "ring.hip", "ipsec.hip", "police.hip", "host.cpp", "shard_cpu.cpp",
+        "sources": ["kernels.hip", "shard.hip", "pktio.hip", "ring.hip", "ipsec.hip", "police.hip", "age.hip", "host.cpp",
+                    "shard_cpu.cpp",
                     "ipsec_cpu.cpp", "iox.cpp", "iox_xdp.cpp", "iox_gpu.cpp", "bindings.cpp"],
         "hip": True,
     },
@@ -165,7 +166,7 @@ def _digest_object(name: str, digest: str, verbose: bool) -> Path:
 # HIP sources whose kernels' register / spill / occupancy figures are recorded at build time
 # (compiler resource remarks -> <module>.resources.json next to the module; the spill guard test
 # tests/test_kernel_resources.py and tools/kernel_resources.py read them)
-RESOURCE_SOURCES = ("kernels.hip", "ring.hip", "police.hip")
+RESOURCE_SOURCES = ("kernels.hip", "ring.hip", "police.hip", "age.hip")
 RESOURCE_FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
                    "LDS Size [bytes/block]")
 
@@ -320,13 +321,17 @@ SANITIZE_TARGETS = {
     # the policer's CPU oracle (host.cpp oracle_police / oracle_police_fix) under its own driver
     "police": {"dir": CSRC / "nfdp", "sources": ["police_stress.cpp", "host.cpp"],
                "flags": ["-D__HIP_PLATFORM_AMD__", "-I", str(ROCM / "include")]},
+    # the flow-aging oracles (host.cpp oracle_age_sweep / oracle_harvest_age) under their own driver
+    "age": {"dir": CSRC / "nfdp", "sources": ["age_stress.cpp", "host.cpp"],
+            "flags": ["-D__HIP_PLATFORM_AMD__", "-I", str(ROCM / "include")]},
 }
 
 
 def build_sanitized(kind: str, verbose: bool = False, target: str = "agent") -> Path:
     """Host-only sanitizer build of a stress driver: the agent (csrc/agent/stress_main.cpp), the
-    native I/O engine (csrc/nfdp/iox_stress.cpp) or the policer's oracle (csrc/nfdp/police_stress.cpp).  GPU sanitizers are unavailable on the MI355X
-    pool; both are pure host code."""
+    native I/O engine (csrc/nfdp/iox_stress.cpp), the policer's oracle (csrc/nfdp/police_stress.cpp) or the
+    flow-aging oracles (csrc/nfdp/age_stress.cpp).  GPU sanitizers are unavailable on the MI355X pool; all of
+    them are pure host code."""
     spec = SANITIZE_TARGETS[target]
     d = spec["dir"]
     out = BUILD / "sanitize" / f"{target}-stress-{kind}"

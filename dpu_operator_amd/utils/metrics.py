@@ -114,6 +114,19 @@ class DataPlaneCollector:
             b, total = h.buckets()
             lat.add_metric([self.name, stage], b, total)
         yield lat
+        # flow aging (DataPlane.enable_flow_aging): families present only while it is on
+        if getattr(dp, "_age_stats", None) is not None:
+            st = dp.flow_age_stats()
+            exp = CounterMetricFamily("dpu_flows_expired", "Flows removed by the idle-timeout sweep", labels=["dataplane"])
+            exp.add_metric([self.name], float(st["expired_total"]))
+            yield exp
+            aged = GaugeMetricFamily("dpu_flows_aged", "Flows armed with an idle timeout", labels=["dataplane"])
+            aged.add_metric([self.name], float(st["armed"]))
+            yield aged
+            sw = GaugeMetricFamily("dpu_flow_sweep_seconds", "Duration of the last aging sweep (launch to completion)",
+                                   labels=["dataplane"])
+            sw.add_metric([self.name], float(st["last_sweep_us"]) * 1e-6)
+            yield sw
 
 
 # drop reasons decided before the flow lookup (ingress_stage)

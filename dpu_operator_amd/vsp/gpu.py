@@ -49,6 +49,7 @@ import logging
 import os
 import re
 import socket
+import threading
 
 import numpy as np
 
@@ -70,7 +71,7 @@ NF_BRIDGE_BASE = 100
 _MUTATING = {"SetNumVfs": "set_num_vfs", "CreateBridgePort": "create_bridge_port",
              "DeleteBridgePort": "delete_bridge_port", "CreateNetworkFunction": "create_network_function",
              "DeleteNetworkFunction": "delete_network_function", "Init": "init", "GpuChain": "on_gpu_chain",
-             "InstallFlows": "_install_flows_rec", "SetVfRate": "set_vf_rate"}
+             "InstallFlows": "_install_flows_rec", "SetVfRate": "set_vf_rate", "RemoveFlows": "_remove_flows_rec"}
 # installs up to this many flows are journaled record-by-record; bigger bulk loads checkpoint
 JOURNAL_FLOWS_MAX = 4096
 
@@ -166,6 +167,9 @@ class GpuVsp(VspBase):
         self.port_state: dict[int, tuple[bool, bool, int]] = {}  # port -> (link, rx, mtu) from the agent
         self.agent_bridge = None
         self._rate_warned = False
+        self._idle_warned = False
+        self.flow_idle_s: dict[bytes, float] = {}   # several GPUs: idle timeouts stored, not enforced
+        self._sweeper = None                        # (thread, stop event) of start_flow_sweeper
         self.journal = Journal(state_dir, "gpu-vsp") if state_dir else None
         self._replaying = False
         self.restored = 0
@@ -341,6 +345,7 @@ class GpuVsp(VspBase):
         return self.agent_bridge
 
     def stop(self) -> None:
+        self.stop_flow_sweeper()
         if self.agent_bridge is not None:
             self.agent_bridge.stop()
             self.agent_bridge = None
@@ -678,25 +683,116 @@ class GpuVsp(VspBase):
             self._replaying = False
 
     # ------------------------------------------------------------------ data path access
-    def install_flows(self, keys: np.ndarray, actions: np.ndarray) -> None:
-        """Install exact-match flows.  Durable with `state_dir`: small installs are journaled,
-        bulk loads (> JOURNAL_FLOWS_MAX) take a checkpoint before returning."""
+    def install_flows(self, keys: np.ndarray, actions: np.ndarray, idle_timeout_s: float = 0) -> None:
+        """Install exact-match flows; with `idle_timeout_s` > 0 they expire after that long without
+        traffic (expire_flows / the sweeper; DataPlane.set_flow_timeout).  Durable with `state_dir`:
+        small installs are journaled, bulk loads (> JOURNAL_FLOWS_MAX) take a checkpoint before
+        returning."""
         keys = np.ascontiguousarray(keys, np.uint32).reshape(-1, 4)
         actions = np.ascontiguousarray(actions, np.uint32).reshape(-1, 4)
+        idle = float(idle_timeout_s)
+        if idle < 0:
+            raise ValueError("idle_timeout_s is negative")
         with self._lock:
             self._ensure_dp()
             self.dp.flows.insert_many(keys, actions)
+            self._apply_idle(keys, idle)
             self._commit()
             if self.journal is None or self._replaying:
                 return
             if len(keys) <= JOURNAL_FLOWS_MAX:
-                self._journal("InstallFlows", (keys.tobytes(), actions.tobytes()))
+                self._journal("InstallFlows", (keys.tobytes(), actions.tobytes(), idle))
             else:
                 self.checkpoint()
 
-    def _install_flows_rec(self, keys: bytes, actions: bytes) -> None:
+    def _install_flows_rec(self, keys: bytes, actions: bytes, idle_timeout_s: float = 0) -> None:
+        # (records written before flows had idle timeouts carry two arguments)
         self.install_flows(np.frombuffer(keys, np.uint32).reshape(-1, 4),
-                           np.frombuffer(actions, np.uint32).reshape(-1, 4))
+                           np.frombuffer(actions, np.uint32).reshape(-1, 4), idle_timeout_s)
+
+    # ------------------------------------------------------------------ flow aging
+    def _aging(self) -> bool:
+        return getattr(self.dp, "_age_stats", None) is not None
+
+    def _apply_idle(self, keys: np.ndarray, idle: float) -> None:
+        """The flows' idle timeout (0: none; a re-installed flow loses the one it had)."""
+        if hasattr(self.dp, "planes"):
+            # several GPUs: with port placement a flow is replicated and idle only when idle on
+            # every plane; stored, not enforced
+            for k in keys:
+                if idle:
+                    self.flow_idle_s[k.tobytes()] = idle
+                else:
+                    self.flow_idle_s.pop(k.tobytes(), None)
+            if idle and not self._idle_warned:
+                self._idle_warned = True
+                log.warning("flow idle timeouts are stored but not enforced with %d GPUs yet", self.gpus)
+            return
+        if idle and not self._aging():
+            self.dp.enable_flow_aging()
+        if self._aging():
+            self.dp.set_flow_timeout(keys, idle)
+
+    def remove_flows(self, keys: np.ndarray) -> int:
+        """Remove exact-match flows by key (IPv6 flows: by their folded key); returns how many were
+        installed.  Journaled like install_flows."""
+        keys = np.ascontiguousarray(keys, np.uint32).reshape(-1, 4)
+        with self._lock:
+            self._ensure_dp()
+            n = int(self.dp.flows.erase_many(keys))
+            f6 = getattr(self.dp, "flows6", None)
+            for k in keys[(keys[:, 3] & np.uint32(T.KEY_V6)) != 0] if f6 else ():
+                f6.pop(tuple(int(x) for x in k), None)
+            for k in keys if self.flow_idle_s else ():
+                self.flow_idle_s.pop(k.tobytes(), None)
+            self._commit()
+            self._journal_removal(keys)
+            return n
+
+    def _remove_flows_rec(self, keys: bytes) -> None:
+        self.remove_flows(np.frombuffer(keys, np.uint32).reshape(-1, 4))
+
+    def _journal_removal(self, keys: np.ndarray) -> None:
+        if self.journal is None or self._replaying or not len(keys):
+            return
+        if len(keys) <= JOURNAL_FLOWS_MAX:
+            self._journal("RemoveFlows", (keys.tobytes(),))
+        else:
+            self.checkpoint()
+
+    def expire_flows(self, now_ns: int | None = None) -> int:
+        """One aging sweep (DataPlane.age_flows): flows idle for their timeout are removed, and
+        the removal is made durable (a restart does not bring them back).  Returns their number."""
+        with self._lock:
+            if self.dp is None or not self._aging():
+                return 0
+            keys = self.dp.age_flows(now_ns)
+            self._journal_removal(keys)
+            return int(len(keys))
+
+    def start_flow_sweeper(self, interval_s: float) -> None:
+        """A daemon thread calling expire_flows every `interval_s` seconds until stop()."""
+        if interval_s <= 0 or self._sweeper is not None:
+            return
+        stop = threading.Event()
+
+        def loop():
+            while not stop.wait(interval_s):
+                try:
+                    self.expire_flows()
+                except Exception:  # noqa: BLE001  (the next sweep finds what this one missed)
+                    log.exception("flow sweep failed")
+
+        t = threading.Thread(target=loop, name="vsp-flow-sweeper", daemon=True)
+        self._sweeper = (t, stop)
+        t.start()
+
+    def stop_flow_sweeper(self) -> None:
+        if self._sweeper is not None:
+            t, stop = self._sweeper
+            self._sweeper = None
+            stop.set()
+            t.join(timeout=10.0)
 
     def process(self, frames: np.ndarray, in_ports) -> tuple[np.ndarray, np.ndarray]:
         """Run a batch through the data plane: frames [n,64] uint8, in_ports [n] -> (out, meta)."""
